@@ -10,6 +10,11 @@ noise frame does: 2.0 MB at q=0.25).  Frames and output buffers are resident
 in HBM when the timed region starts.  A step = one pass over the batch.
 MP counted once per image (decoded W x H).
 
+A plain run sets up, warms up, times the steps and prints the line (roofline
+and per-kernel figures come from the HIP events of the timed steps).  --full
+adds the legs that take runs of their own: host_io, pool, e2e and the CPU
+baselines.  --dump-outputs DIR writes what the last timed step computed.
+
 Multi-GPU: one process per GPU (torchrun); each rank owns its own frames
 (file-list sharding, no data-path collective) -> weak scaling.  The barrier
 and the max-over-ranks reduction of the step time are the only collectives,
@@ -408,11 +413,59 @@ def e2e_cpu_baseline(srcs, n_sample, threads):
                       f"{dt:.2f} s wall"}
 
 
+DUMP_SAMPLE_IMAGES = 12      # --dump-outputs: images whose JPEG bytes are written out whole
+DUMP_SAMPLE_BYTES = 12 << 20  # ... and the cap on those bytes (float32: 48 MiB of the 64 MB allowed)
+
+
+def dump_outputs(path, res, outs):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, as float64 / float32 .npy files.  Per image (all of them): the result
+    fields of icx_compress_jpg_batch, and two checksums of the JPEG bytes
+    outs[i][:out_len] (byte sum; sum of byte x (1 + position mod 251), both
+    exact in float64).  The bytes themselves for a fixed, seeded sample of
+    images (1000 x ~0.86 MB does not fit), concatenated in index order."""
+    os.makedirs(path, exist_ok=True)
+    n = len(res)
+    lens = [int(r["out_len"]) for r in res]
+    f64 = lambda v: np.asarray(v, dtype=np.float64)  # noqa: E731
+    cols = {"out_len": lens, "success": [r["success"] for r in res], "status": [r["status"] for r in res],
+            "cache_hit": [r["cache_hit"] for r in res], "encodes": [r["encodes"] for r in res],
+            "learned_quality": [r["learned"].quality for r in res],
+            "learned_scale": [r["learned"].scale for r in res]}
+    for name, v in cols.items():
+        np.save(os.path.join(path, name + ".npy"), f64(v))
+    weight = (torch.arange(outs.shape[1], device=outs.device, dtype=torch.int64) % 251) + 1
+    sums = torch.zeros((n, 2), dtype=torch.int64, device=outs.device)
+    for i in range(n):
+        b = outs[i, :lens[i]].to(torch.int64)
+        sums[i, 0] = b.sum()
+        sums[i, 1] = (b * weight[:lens[i]]).sum()
+    sums = sums.cpu().numpy()
+    np.save(os.path.join(path, "jpeg_byte_sum.npy"), f64(sums[:, 0]))
+    np.save(os.path.join(path, "jpeg_weighted_sum.npy"), f64(sums[:, 1]))
+    pick = np.sort(np.random.default_rng(12345).permutation(n)[:DUMP_SAMPLE_IMAGES])
+    parts, room = [], DUMP_SAMPLE_BYTES
+    for i in pick:
+        part = outs[int(i), :min(lens[i], room)].cpu().numpy().astype(np.float32)
+        parts.append(part)
+        room -= len(part)
+    np.save(os.path.join(path, "jpeg_sample_index.npy"), f64(pick))
+    np.save(os.path.join(path, "jpeg_sample_bytes.npy"),
+            np.concatenate(parts) if parts else np.zeros(0, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the other legs (host_io, pool, e2e, the CPU baselines); "
+                         "without it only the headline is set up, warmed up and timed, and the options of "
+                         "those legs have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (per-image results, checksums "
+                         "of every JPEG, the bytes of a seeded sample) as DIR/<name>.npy")
     ap.add_argument("--images", type=int, default=1000, help="4K frames per GPU per step")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="4K frames for the CPU baseline (0 = 20 per host core, at least 320: ~10 s of wall time)")
@@ -486,6 +539,8 @@ def main():
     dt = time.perf_counter() - t0
     codec.profile(False)
     validate()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch.results(), outs)
     if dist:
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -557,12 +612,25 @@ def main():
                         **({"algo_bytes": int(bytes_of[k])} if k in bytes_of else {})}
                     for k, v in kstats.items()},
     }
+    if args.full:
+        batch = None  # the legs prepare batches of their own
+        other_legs(args, line, value, codec, dev, frames, cached, dist, rank, world, local)
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    codec.close()
+    if dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def other_legs(args, line, value, codec, dev, frames, cached, dist, rank, world, local):
+    """--full: everything the line carries beside the headline, each a run of
+    its own after the headline's timed region."""
     # the host-fed legs and e2e run on every rank (each over its own link and
     # GPU, together), timed between barriers, max over ranks
     n_host = args.host_io_frames if args.host_io_frames >= 0 else (1000 if world == 1 else max(200, 2000 // world))
     n_host = min(n_host, args.images)
     if n_host and not args.host_io:
-        batch = None
         hf = host_frames(frames, n_host)
         line["host_io"] = host_io_leg(codec, frames, hf, args.steps, args.warmup, cached, dist, world)
         if args.pool_devices != "none":
@@ -572,7 +640,6 @@ def main():
         hf = None
     cores, cores_how = host_cores()
     if args.e2e and not args.host_io:
-        batch = None
         line["e2e"] = e2e_leg(codec, dev, frames, min(args.e2e, args.images), args.steps,
                               cpu_sample=0 if (args.no_cpu_baseline or rank) else max(64, 4 * cores), threads=cores,
                               dist=dist, world=world)
@@ -585,12 +652,6 @@ def main():
         cb, _ = cpu_baseline(frames, args.cpu_sample or max(320, 20 * cores), cores, cores_how)
         line["cpu_baseline"] = cb
         line["speedup_vs_cpu"] = round(value / cb["value"], 1)
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    codec.close()
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -16,7 +16,7 @@ for r in $(seq $ROUNDS); do
       *.so:*) lib=image-compression_amd/${v%%:*}; envs=${v#*:}; envs=${envs//,/ } ;;
       *=*) lib=image-compression_amd/lib/libicx.so; envs=${v//,/ } ;;
     esac
-    env $envs ICX_LIB=$(pwd)/$lib timeout -k 10 240 python bench.py --images 1000 --e2e ${FRAMES:-1000} --steps ${STEPS:-3} \
+    env $envs ICX_LIB=$(pwd)/$lib timeout -k 10 240 python bench.py --full --images 1000 --e2e ${FRAMES:-1000} --steps ${STEPS:-3} \
         --warmup 1 --no-cpu-baseline --host-io-frames 0 --pool-devices none --profile 0 \
         > gpurun_out/abe.json 2> gpurun_out/abe.err || { echo "$v failed"; tail -5 gpurun_out/abe.err; exit 1; }
     python3 - "$v" <<'PY'

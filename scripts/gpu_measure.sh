@@ -13,6 +13,7 @@ if [ -z "$SKIP_TESTS" ]; then
       > gpurun_out/pytest_gpu_${TAG}.log 2>&1 || { echo "pytest failed"; tail -30 gpurun_out/pytest_gpu_${TAG}.log; exit 1; }
   tail -2 gpurun_out/pytest_gpu_${TAG}.log
 fi
+BENCH_ARGS=${BENCH_ARGS:---full --steps 20 --warmup 5}  # every leg of the line, not the headline alone
 timeout -k 10 400 python bench.py ${BENCH_ARGS:---steps 20 --warmup 5} > gpurun_out/bench_${TAG}.json \
     2> gpurun_out/bench_${TAG}.err || { echo "bench failed rc=$?"; tail -20 gpurun_out/bench_${TAG}.err; exit 1; }
 cat gpurun_out/bench_${TAG}.json

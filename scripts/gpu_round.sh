@@ -21,6 +21,7 @@ if [ -z "$SKIP_TESTS" ]; then
   tail -15 gpurun_out/pytest_gpu_${TAG}.log
   [ $rc -eq 0 ] || { echo "pytest rc=$rc"; exit $rc; }
 fi
+BENCH_ARGS=${BENCH_ARGS:---full --steps 20 --warmup 5}  # every leg of the line, not the headline alone
 timeout -k 10 ${T_BENCH:-400} python bench.py ${BENCH_ARGS:---steps 20 --warmup 5} > gpurun_out/bench_${TAG}.json \
     2> gpurun_out/bench_${TAG}.err || { echo "bench failed rc=$?"; tail -20 gpurun_out/bench_${TAG}.err; exit 1; }
 cat gpurun_out/bench_${TAG}.json
