@@ -240,8 +240,9 @@ int host_threads()
 }
 
 // Files whose entropy decode runs on host threads: progressive files (SOF2,
-// icx_progressive.cpp: one sequential walk per scan), and sequential files
-// the device's decode flagged (icx_seqdecode.cpp: IJG 6b's recovery from
+// icx_progressive.cpp: one sequential walk per scan), sequential files that
+// select more Huffman tables than DecTab holds (dec_tables_fit), and
+// sequential files the device's decode flagged (icx_seqdecode.cpp: IJG 6b's recovery from
 // truncated scans, bad codes and restart markers out of sequence).  Each
 // file's coefficients go straight into pinned staging, in the layout
 // k_dec_write leaves for baseline files; one copy per file takes the
@@ -471,7 +472,8 @@ icx_status run_decode_impl(icx_ctx* c, icx_decode_job* jobs, int n, int16_t* coe
             j.status = ICX_E_BUFFER;
             continue;
         }
-        (it.J.progressive ? prog : items).push_back(it);
+        // more Huffman tables than DecTab has slots: host entropy decode, device pixels
+        (it.J.progressive || !dec_tables_fit(it.J) ? prog : items).push_back(it);
     }
     if (!prog.empty())
         if (icx_status s = run_host_entropy(c, prog, coef_out, coef_cap)) return s;

@@ -276,6 +276,19 @@ void build_dec_lean(const DecHuff& h, bool ac, DecLean& lean)
         for (int i = 0; i < (1 << (16 - DEC_LUT_BITS)); i++) lean.lut2[k][i] = conv(h.lut2[k][i]);
 }
 
+int dec_distinct_tables(const JpegHeader& J)
+{
+    bool seen[2][4] = {};
+    int n = 0;
+    for (int c = 0; c < J.ncomp && c < 4; c++)
+        for (int ac = 0; ac < 2; ac++) {
+            bool& s = seen[ac][(ac ? J.ta[c] : J.td[c]) & 3];
+            n += !s;
+            s = true;
+        }
+    return n;
+}
+
 bool build_dec_tab(const JpegHeader& J, DecTab& T)
 {
     memset(&T, 0, sizeof(T));
@@ -288,7 +301,7 @@ bool build_dec_tab(const JpegHeader& J, DecTab& T)
             const int id = ac ? J.ta[c] : J.td[c];
             int& sl = slot_of[ac][id];
             if (sl < 0) {
-                if (ntab == 4) return false;
+                if (ntab == DEC_TAB_SLOTS) return false;  // callers route such files to seq_decode
                 sl = ntab++;
                 if (!build_dec_huff(J.hbits[ac][id], J.hvals[ac][id], J.hn[ac][id], T.h[sl], T.slow[sl])) return false;
                 if (!ac)  // jpeg_make_d_derived_tbl: DC symbols are 0..15 (12..15 the walks leave to seq_decode)

@@ -48,8 +48,18 @@ int colour_space(const JpegHeader& J, bool jfif, bool exif, bool adobe, int tran
 bool build_dec_huff(const uint8_t* bits, const uint8_t* vals, int n, DecHuff& t, DecSlow& slow);
 void build_dec_lean(const DecHuff& h, bool ac, DecLean& lean);
 
+// Distinct (class, id) Huffman tables the scan's components select.  DecTab
+// has DEC_TAB_SLOTS slots (2-bit selectors, four first levels in k_dec_write's
+// LDS): a file that uses more - each of three components on a DC and an AC
+// table of its own, say - is valid but rare, and takes the host entropy
+// decode (seq_decode, which indexes tables by id) with the device's IDCT and
+// colour passes, as progressive files do.
+constexpr int DEC_TAB_SLOTS = 4;
+int dec_distinct_tables(const JpegHeader& J);
+inline bool dec_tables_fit(const JpegHeader& J) { return dec_distinct_tables(J) <= DEC_TAB_SLOTS; }
+
 // Per-image decode tables (distinct Huffman tables + per-component selectors,
-// dequantisation per component).
+// dequantisation per component).  J's tables must fit (dec_tables_fit).
 bool build_dec_tab(const JpegHeader& J, DecTab& T);
 
 // DecTab::sel packed 4 bits per entry, as dec_walk takes it.

@@ -36,6 +36,15 @@ extern "C" int dec_emu_coefs(const uint8_t* jpg, size_t len, int16_t* out, size_
     JpegHeader J;
     icx_status st = parse_jpeg(jpg, len, len, J);
     if (st) return (int)st;
+    if (!dec_tables_fit(J)) {  // as run_decode_impl: more tables than DecTab has slots -> the host route
+        if (iterations) *iterations = 0;
+        std::vector<int32_t> hdc(nblocks_cap);
+        const int hs = J.ncomp == 3 ? J.hs[0] : 1, vs = J.ncomp == 3 ? J.vs[0] : 1;
+        const size_t nb = (size_t)((J.w + 8 * hs - 1) / (8 * hs)) * ((J.h + 8 * vs - 1) / (8 * vs)) *
+                          (J.ncomp == 3 ? hs * vs + 2 : J.ncomp == 4 ? 4 : 1);
+        if (nb > nblocks_cap) return ICX_E_BUFFER;
+        return (int)seq_decode(jpg, len, J, out, hdc.data());
+    }
     static DecTab T;
     if (!build_dec_tab(J, T)) return ICX_E_CORRUPT;
     const uint32_t sel = dec_selector(T);
@@ -217,6 +226,17 @@ extern "C" int dec_emu_coefs(const uint8_t* jpg, size_t len, int16_t* out, size_
     }
     memcpy(out, coefs.data(), coefs.size() * sizeof(int16_t));
     return 0;
+}
+
+// The route run_decode_impl gives a file: 0 the device's entropy decode, 1 the
+// host's (progressive, or more Huffman tables than DecTab has slots), negative:
+// the header's status.
+extern "C" int dec_emu_route(const uint8_t* jpg, size_t len)
+{
+    JpegHeader J;
+    icx_status st = parse_jpeg(jpg, len, len, J);
+    if (st) return -(int)st;
+    return J.progressive || !dec_tables_fit(J) ? 1 : 0;
 }
 
 // DecLeanWalker (k_dec_init / k_dec_sync) against DecWalker<false> (the write

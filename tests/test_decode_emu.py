@@ -27,7 +27,8 @@ def emu():
     flags = os.environ.get("ICX_EMU_FLAGS", "").split()
     lib = os.path.join(BUILD, "dec_emu%s.so" % ("_" + "_".join(f.strip("-").replace("=", "") for f in flags)
                                                  if flags else ""))
-    srcs = [os.path.join(ROOT, "tests", "dec_emu.cpp"), os.path.join(CSRC, "icx_jpeg_parse.cpp")]
+    srcs = [os.path.join(ROOT, "tests", "dec_emu.cpp"), os.path.join(CSRC, "icx_jpeg_parse.cpp"),
+            os.path.join(CSRC, "icx_seqdecode.cpp")]
     deps = srcs + [os.path.join(CSRC, "icx_decode.h"), os.path.join(CSRC, "icx_jpeg_parse.h")]
     if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(f) for f in deps):
         # built under a name of this process, then renamed into place: test
@@ -80,7 +81,8 @@ def test_fuzzed_streams_never_read_out_of_bounds(oracle, tmp_path):
     without an out-of-bounds access.  Guards the device kernels' indexing,
     which share this code."""
     lib = os.path.join(BUILD, "dec_emu_asan.so")
-    srcs = [os.path.join(ROOT, "tests", "dec_emu.cpp"), os.path.join(CSRC, "icx_jpeg_parse.cpp")]
+    srcs = [os.path.join(ROOT, "tests", "dec_emu.cpp"), os.path.join(CSRC, "icx_jpeg_parse.cpp"),
+            os.path.join(CSRC, "icx_seqdecode.cpp")]
     exe = str(tmp_path / "fuzz")
     main = tmp_path / "fuzz_main.cpp"
     main.write_text(r'''

@@ -72,6 +72,19 @@ def test_decode_then_fit_in_hbm_matches_oracle(codec, oracle, dgolden):
         assert r["success"] == o["success"] and r.get("data") == o["data"], name
 
 
+def _status_class(code):
+    """Device status or oracle return code (oracle/icx_oracle.h uses the
+    numbers of include/icx.h: 0 ok, 5 not read here, 6 corrupt, 8 refused) as
+    one of "ok" / "corrupt" / "unsupported"; anything else stays itself."""
+    if code == N.OK:
+        return "ok"
+    if code == N.E_CORRUPT:
+        return "corrupt"
+    if code in (N.E_UNSUPPORTED, N.E_REFUSED):
+        return "unsupported"
+    return code
+
+
 def _jpeg(rgb, **kw):
     from PIL import Image
     b = io.BytesIO()
@@ -147,7 +160,8 @@ def test_decode_of_own_encodes_round_trip(codec, oracle):
 def test_decode_refusals_and_corrupt_input(codec, oracle, dgolden):
     """Headers the JDK reader cannot read are corrupt; a scan cut short
     decodes as that reader decodes it (IJG 6b's recovery: the oracle's
-    pixels); neither spoils the batch."""
+    pixels); neither spoils the batch.  The device's verdict on each bad
+    header is the oracle's (corrupt / unsupported)."""
     meta, jpgs, _ = dgolden
     good = jpgs["c130x250_s2_q95"]
     cut = [good[: len(good) // 2], good[: len(good) - 3]]
@@ -156,8 +170,10 @@ def test_decode_refusals_and_corrupt_input(codec, oracle, dgolden):
     for d, (st, img) in zip(cut, res):
         rc, ref = oracle.jpeg_decode(d)
         assert st == N.OK and rc == 0 and np.array_equal(img, ref)
-    for st, img in res[len(cut):-1]:
-        assert st in (N.E_CORRUPT, N.E_UNSUPPORTED), st
+    for d, (st, img) in zip(bad, res[len(cut):-1]):
+        rc, _ = oracle.jpeg_decode(d)
+        assert st in (N.E_CORRUPT, N.E_UNSUPPORTED, N.E_REFUSED), st
+        assert _status_class(st) == _status_class(rc), (st, rc)
     assert res[-1][0] == N.OK  # a bad file does not spoil the batch
 
 
@@ -165,8 +181,19 @@ def test_decode_fuzzed_batch(codec, oracle, dgolden):
     """400 corrupted files in one device batch (flipped entropy bytes,
     truncation, stray RSTn/EOI/fill markers, corrupted headers): every file
     ends with OK, UNSUPPORTED or CORRUPT, a bad file never spoils its
-    neighbours, and whatever the device accepts decodes exactly as the oracle
-    does."""
+    neighbours, whatever the device accepts decodes exactly as the oracle
+    does, and the device's verdict is the oracle's on every file: OK with OK,
+    CORRUPT with corrupt (6), UNSUPPORTED / REFUSED with not-read-here /
+    refused (5 / 8).
+
+    ORACLE_DIFFERS names the files on which the two CPU references part and
+    the device sides with libjpeg (at most 2 % of the 400 may stand here):
+     * 363: a chroma sampling factor of 7.  libjpeg refuses factors above 4
+       (jdinput.c initial_setup, JERR_BAD_SAMPLING: the JDK reader throws;
+       Pillow's libjpeg-turbo raises too), parse_jpeg reports corrupt; the
+       oracle's header parser has no such check and answers 5."""
+    ORACLE_DIFFERS = {363: N.E_CORRUPT}
+    assert len(ORACLE_DIFFERS) <= 8
     meta, jpgs, pxs = dgolden
     rng = np.random.default_rng(99)
     names = [k for k in jpgs if not meta["cases"][k].get("unsupported")]
@@ -195,9 +222,13 @@ def test_decode_fuzzed_batch(codec, oracle, dgolden):
         assert st in (N.OK, N.E_UNSUPPORTED, N.E_CORRUPT, N.E_REFUSED), (i, st)
         if i % 5 == 4:
             assert st == N.OK and np.array_equal(img, pxs[names[i % len(names)]]), i
+        rc, ref = oracle.jpeg_decode(d)
+        if i in ORACLE_DIFFERS:
+            assert st == ORACLE_DIFFERS[i] and _status_class(rc) != _status_class(st), (i, st, rc)
+            continue
+        assert _status_class(st) == _status_class(rc), (i, st, rc)
         if st == N.OK:
-            rc, ref = oracle.jpeg_decode(d)
-            assert rc == 0 and np.array_equal(img, ref), i
+            assert np.array_equal(img, ref), i
             ok += 1
     assert ok >= 240  # damaged entropy data decodes (6b recovery); header damage may not
 

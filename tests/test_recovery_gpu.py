@@ -51,6 +51,24 @@ def test_recovery_fixtures_in_one_batch(codec, oracle, recovery):
     assert n_ok >= 190
 
 
+def test_intact_fixtures_stay_on_the_device_route(codec, oracle, recovery):
+    """The *_intact fixtures alone: decoded by the device's entropy decode,
+    none handed to the host recovery (the dec_recovered counter stays 0) - a
+    recovery flag that fired on intact files would change no pixel and only
+    cost throughput.  One damaged fixture moves the counter."""
+    meta, jpgs, z = recovery
+    names = sorted(k for k in jpgs if k.endswith("_intact"))
+    assert len(names) >= 5
+    codec.profile_reset()
+    res = codec.decode_jpg_batch([jpgs[k] for k in names], subsampling=1)
+    assert codec.profile_query("dec_recovered")["units"] == 0
+    for name, (st, img) in zip(names, res):
+        rc, ref = oracle.jpeg_decode(jpgs[name])
+        assert st == N.OK and rc == 0 and np.array_equal(img, ref), name
+    st, _ = codec.decode_jpg_batch([jpgs["c420_200x136_cut600"]], subsampling=1)[0]
+    assert st == N.OK and codec.profile_query("dec_recovered")["units"] >= 1
+
+
 def test_recovery_coefficients_match_oracle(codec, oracle, recovery):
     meta, jpgs, _ = recovery
     for name in sorted(jpgs):
@@ -81,16 +99,24 @@ def _damage(data, rng):
 @pytest.mark.parametrize("kind", ["smooth", "noise"])
 def test_recovery_4k_matches_oracle(codec, oracle, kind):
     """4K q95 frames (the e2e leg's sources) damaged, with and without DRI:
-    the device decode equals the oracle's, a whole batch at once."""
+    the device decode equals the oracle's, a whole batch at once.  The
+    undamaged pair first: it stays on the device route (dec_recovered 0)."""
     import io
     from PIL import Image
     rng = np.random.default_rng(5)
     img = (smooth if kind == "smooth" else noise)(2160, 3840, 17)
-    datas = []
+    datas, intact = [], []
     for kw in ({}, {"restart_marker_rows": 2}):
         buf = io.BytesIO()
         Image.fromarray(img[:, :, ::-1]).save(buf, "JPEG", quality=95, subsampling=2, **kw)
+        intact.append(buf.getvalue())
         datas += list(_damage(buf.getvalue(), rng).values())
+    codec.profile_reset()
+    res = codec.decode_jpg_batch(intact, subsampling=1)
+    assert codec.profile_query("dec_recovered")["units"] == 0
+    rc, ref = oracle.jpeg_decode(intact[0])  # (the DRI twin holds the same coefficients)
+    for st, px in res:
+        assert st == N.OK and rc == 0 and np.array_equal(px, ref)
     res = codec.decode_jpg_batch(datas, subsampling=1)
     for i, (d, (st, px)) in enumerate(zip(datas, res)):
         rc, ref = oracle.jpeg_decode(d)
