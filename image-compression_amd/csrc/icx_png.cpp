@@ -34,6 +34,10 @@
 // caller's buffer: no image-sized temporary.  The caller's thread does the
 // work; ctypes releases the GIL, so the batch driver's writer pool runs one
 // image per thread.
+//
+// icx_png_encode_filtered is the same writer from rows that are filtered
+// already (on the device: icx_pngfilter.hip, icx_png_filter_batch /
+// icx_png_fit_filter_batch); both go through PngWriter below.
 #include <zlib.h>
 
 #include <algorithm>
@@ -42,6 +46,7 @@
 #include <vector>
 
 #include "icx_context.h"
+#include "icx_pngfilter.h"
 
 namespace {
 
@@ -203,6 +208,31 @@ size_t close_chunk(uint8_t* p, const char* tag, size_t len)
 
 }  // namespace
 
+// The device filter's view of a raster (icx_pngfilter.h): the same choices as
+// icx_png_encode makes below.
+void icx::png_filter_desc(const icx_image* img, icx::PngFilterArgs* a)
+{
+    const bool pal = img->fmt == ICX_INDEXED8 || img->fmt == ICX_BINARY1;
+    const PalOut po = pal ? pal_out(img) : PalOut{};
+    a->w = img->width;
+    a->h = img->height;
+    a->n = (int32_t)png_row_bytes(img);
+    a->bpp = pal && po.ctype == 4 ? 2 : png_bpp(img->fmt);
+    a->depth = pal ? po.depth : 8;
+    a->force0 = pal && po.ctype == 3;
+    a->pal_len = pal ? img->palette_len : 0;
+    switch (img->fmt) {
+    case ICX_GRAY16: a->mode = icx::PF_SWAP16; break;
+    case ICX_BGR24: a->mode = icx::PF_BGR24; break;
+    case ICX_XRGB32: a->mode = icx::PF_XRGB32; break;
+    case ICX_ARGB32: a->mode = icx::PF_ARGB32; break;
+    case ICX_ABGR32: a->mode = icx::PF_ABGR32; break;
+    case ICX_INDEXED8:
+    case ICX_BINARY1: a->mode = po.ctype == 4 ? icx::PF_PAL_GA : po.depth == 8 ? icx::PF_COPY : icx::PF_PACK; break;
+    default: a->mode = icx::PF_COPY;  // GRAY8, RGB24, RGBA32
+    }
+}
+
 extern "C" {
 
 // The whole filtered image (raw bytes) up to 1 GiB: zlib's 32-bit counters.
@@ -230,75 +260,74 @@ size_t icx_png_bound(const icx_image* img)
     return 8 + 25 + z + 12 * (z / kIdat + 1) + 12 + 64 + 12 + 3 * 256 + 12 + 256;  // + PLTE, tRNS
 }
 
-icx_status icx_png_encode(const icx_image* img, int32_t level, uint8_t* out, size_t cap, size_t* out_len)
-{
-    if (!img || !img->px || !out || !out_len) return ICX_E_NULL;
-    if (img->width <= 0 || img->height <= 0 || img->fmt < ICX_BGR24 || img->fmt > ICX_BINARY1 ||
-        img->stride < img->width * src_bpp(img->fmt) || level < -1 || level > 9)
-        return ICX_E_INVALID;
-    if (icx::is_device_ptr(img->px)) return ICX_E_INVALID;  // host rows only
-    if (!palette_ok(img)) return ICX_E_INVALID;             // no map, or more entries than the depth holds
-    const size_t need = icx_png_bound(img);
-    if (need == 0) return ICX_E_UNSUPPORTED;  // over kMaxRaw
-    *out_len = need;
-    if (cap < need) return ICX_E_BUFFER;
-    const bool pal = img->fmt == ICX_INDEXED8 || img->fmt == ICX_BINARY1;
-    const PalOut po = pal ? pal_out(img) : PalOut{};
-    const int bpp = pal && po.ctype == 4 ? 2 : png_bpp(img->fmt);
-    const int n = (int)png_row_bytes(img);
-    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-    memcpy(out, sig, 8);
-    size_t pos = 8;
-    uint8_t* ih = out + pos + 8;
-    put32(ih, (uint32_t)img->width);
-    put32(ih + 4, (uint32_t)img->height);
-    ih[8] = pal ? (uint8_t)po.depth : img->fmt == ICX_GRAY16 ? 16 : 8;                // bit depth
-    ih[9] = pal ? (uint8_t)po.ctype : (uint8_t)(bpp <= 2 ? 0 : bpp == 3 ? 2 : 6);    // colour type
-    ih[10] = ih[11] = ih[12] = 0;                             // deflate, adaptive filtering, no interlace
-    pos += close_chunk(out + pos, "IHDR", 13);
-    if (pal && po.ctype == 3) {  // PLTE = the whole map, tRNS = its alphas
-        uint8_t* p = out + pos + 8;
-        for (int i = 0; i < img->palette_len; i++) {
-            p[3 * i] = (uint8_t)(img->palette[i] >> 16);
-            p[3 * i + 1] = (uint8_t)(img->palette[i] >> 8);
-            p[3 * i + 2] = (uint8_t)img->palette[i];
-        }
-        pos += close_chunk(out + pos, "PLTE", 3 * (size_t)img->palette_len);
-        if (po.alpha) {
-            p = out + pos + 8;
-            for (int i = 0; i < img->palette_len; i++) p[i] = (uint8_t)(img->palette[i] >> 24);
-            pos += close_chunk(out + pos, "tRNS", (size_t)img->palette_len);
+// The file around the filtered rows, shared by icx_png_encode and
+// icx_png_encode_filtered: signature, IHDR, PLTE / tRNS, then one zlib stream
+// fed one filtered row (n + 1 bytes) per deflate call and cut into IDAT
+// chunks, IEND.  Both entry points feed the same bytes in the same pieces, so
+// their files are equal by construction.
+namespace {
+
+struct PngWriter {
+    uint8_t* out;
+    size_t cap, pos = 0;
+    z_stream z{};
+    uint8_t* idat = nullptr;
+    size_t ccap = 0;
+    int zr = Z_OK;
+    bool finished = false, open = false;
+
+    // this chunk's data capacity: kIdat, or less when the caller's buffer ends
+    // first (then a full chunk means the buffer is exhausted)
+    size_t room(size_t at) const { return cap > at + 32 ? std::min(kIdat, cap - at - 32) : 0; }
+
+    void header(const icx_image* img, bool pal, const PalOut& po, int bpp)
+    {
+        static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+        memcpy(out, sig, 8);
+        pos = 8;
+        uint8_t* ih = out + pos + 8;
+        put32(ih, (uint32_t)img->width);
+        put32(ih + 4, (uint32_t)img->height);
+        ih[8] = pal ? (uint8_t)po.depth : img->fmt == ICX_GRAY16 ? 16 : 8;                // bit depth
+        ih[9] = pal ? (uint8_t)po.ctype : (uint8_t)(bpp <= 2 ? 0 : bpp == 3 ? 2 : 6);    // colour type
+        ih[10] = ih[11] = ih[12] = 0;                             // deflate, adaptive filtering, no interlace
+        pos += close_chunk(out + pos, "IHDR", 13);
+        if (pal && po.ctype == 3) {  // PLTE = the whole map, tRNS = its alphas
+            uint8_t* p = out + pos + 8;
+            for (int i = 0; i < img->palette_len; i++) {
+                p[3 * i] = (uint8_t)(img->palette[i] >> 16);
+                p[3 * i + 1] = (uint8_t)(img->palette[i] >> 8);
+                p[3 * i + 2] = (uint8_t)img->palette[i];
+            }
+            pos += close_chunk(out + pos, "PLTE", 3 * (size_t)img->palette_len);
+            if (po.alpha) {
+                p = out + pos + 8;
+                for (int i = 0; i < img->palette_len; i++) p[i] = (uint8_t)(img->palette[i] >> 24);
+                pos += close_chunk(out + pos, "tRNS", (size_t)img->palette_len);
+            }
         }
     }
 
-    z_stream z{};
-    if (deflateInit(&z, level < 0 ? kDefaultLevel : level) != Z_OK) return ICX_E_NOMEM;
-    std::vector<uint8_t> rows(3 * (size_t)n + 1);
-    uint8_t *cur = rows.data(), *prev = cur + n, *filt = prev + n;
-    memset(prev, 0, (size_t)n);
-    // deflate straight into IDAT chunks of kIdat data bytes: a full chunk is
-    // closed (length, tag, CRC) and the next one opened behind it
-    uint8_t* idat = out + pos;
-    // this chunk's data capacity: kIdat, or less when the caller's buffer ends
-    // first (then a full chunk means the buffer is exhausted)
-    auto room = [&](size_t at) -> size_t { return cap > at + 32 ? std::min(kIdat, cap - at - 32) : 0; };
-    size_t ccap = room(pos);
-    z.next_out = idat + 8;
-    z.avail_out = (uInt)ccap;
-    int zr = Z_OK;
-    bool finished = false;
-    for (int y = 0; y < img->height && zr == Z_OK; y++) {
-        if (pal) convert_pal_row(img->px + (size_t)y * img->stride, img, po, cur);
-        else convert_row(img->px + (size_t)y * img->stride, img->width, img->fmt, cur);
-        if (pal && po.ctype == 3) {  // RowFilter: "Use type 0 for palette images"
-            filt[0] = 0;
-            memcpy(filt + 1, cur, (size_t)n);
-        } else {
-            filter_row(cur, prev, n, bpp, filt);
-        }
-        z.next_in = filt;
-        z.avail_in = (uInt)n + 1;
-        const int flush = y + 1 == img->height ? Z_FINISH : Z_NO_FLUSH;
+    bool begin(int level)
+    {
+        if (deflateInit(&z, level < 0 ? kDefaultLevel : level) != Z_OK) return false;
+        open = true;
+        // deflate straight into IDAT chunks of kIdat data bytes: a full chunk is
+        // closed (length, tag, CRC) and the next one opened behind it
+        idat = out + pos;
+        ccap = room(pos);
+        z.next_out = idat + 8;
+        z.avail_out = (uInt)ccap;
+        return true;
+    }
+
+    // One filtered row (type + residuals) into the stream; false once it failed.
+    bool row(const uint8_t* filt, size_t len, bool last)
+    {
+        if (zr != Z_OK) return false;
+        z.next_in = const_cast<uint8_t*>(filt);
+        z.avail_in = (uInt)len;
+        const int flush = last ? Z_FINISH : Z_NO_FLUSH;
         for (;;) {
             zr = deflate(&z, flush);
             if (zr == Z_STREAM_END) {
@@ -318,16 +347,92 @@ icx_status icx_png_encode(const icx_image* img, int32_t level, uint8_t* out, siz
             z.next_out = idat + 8;
             z.avail_out = (uInt)ccap;
         }
+        return zr == Z_OK;
+    }
+
+    icx_status end(size_t* out_len)
+    {
+        const size_t last = ccap - z.avail_out;
+        const bool ok = finished && z.avail_in == 0 && zr == Z_OK;
+        deflateEnd(&z);
+        open = false;
+        if (!ok) return ICX_E_BUFFER;
+        if (last > 0) pos += close_chunk(idat, "IDAT", last);
+        pos += close_chunk(out + pos, "IEND", 0);
+        *out_len = pos;
+        return ICX_OK;
+    }
+};
+
+}  // namespace
+
+size_t icx_png_filtered_size(const icx_image* img)
+{
+    if (icx_png_bound(img) == 0) return 0;
+    return (size_t)img->height * (png_row_bytes(img) + 1);
+}
+
+icx_status icx_png_encode(const icx_image* img, int32_t level, uint8_t* out, size_t cap, size_t* out_len)
+{
+    if (!img || !img->px || !out || !out_len) return ICX_E_NULL;
+    if (img->width <= 0 || img->height <= 0 || img->fmt < ICX_BGR24 || img->fmt > ICX_BINARY1 ||
+        img->stride < img->width * src_bpp(img->fmt) || level < -1 || level > 9)
+        return ICX_E_INVALID;
+    if (icx::is_device_ptr(img->px)) return ICX_E_INVALID;  // host rows only
+    if (!palette_ok(img)) return ICX_E_INVALID;             // no map, or more entries than the depth holds
+    const size_t need = icx_png_bound(img);
+    if (need == 0) return ICX_E_UNSUPPORTED;  // over kMaxRaw
+    *out_len = need;
+    if (cap < need) return ICX_E_BUFFER;
+    const bool pal = img->fmt == ICX_INDEXED8 || img->fmt == ICX_BINARY1;
+    const PalOut po = pal ? pal_out(img) : PalOut{};
+    const int bpp = pal && po.ctype == 4 ? 2 : png_bpp(img->fmt);
+    const int n = (int)png_row_bytes(img);
+    PngWriter w{out, cap};
+    w.header(img, pal, po, bpp);
+    if (!w.begin(level)) return ICX_E_NOMEM;
+    std::vector<uint8_t> rows(3 * (size_t)n + 1);
+    uint8_t *cur = rows.data(), *prev = cur + n, *filt = prev + n;
+    memset(prev, 0, (size_t)n);
+    for (int y = 0; y < img->height; y++) {
+        if (pal) convert_pal_row(img->px + (size_t)y * img->stride, img, po, cur);
+        else convert_row(img->px + (size_t)y * img->stride, img->width, img->fmt, cur);
+        if (pal && po.ctype == 3) {  // RowFilter: "Use type 0 for palette images"
+            filt[0] = 0;
+            memcpy(filt + 1, cur, (size_t)n);
+        } else {
+            filter_row(cur, prev, n, bpp, filt);
+        }
+        if (!w.row(filt, (size_t)n + 1, y + 1 == img->height)) break;
         std::swap(cur, prev);
     }
-    const size_t last = ccap - z.avail_out;
-    const bool ok = finished && z.avail_in == 0 && zr == Z_OK;
-    deflateEnd(&z);
-    if (!ok) return ICX_E_BUFFER;
-    if (last > 0) pos += close_chunk(idat, "IDAT", last);
-    pos += close_chunk(out + pos, "IEND", 0);
-    *out_len = pos;
-    return ICX_OK;
+    return w.end(out_len);
+}
+
+icx_status icx_png_encode_filtered(const icx_image* meta, const uint8_t* filtered, size_t len, int32_t level,
+                                   uint8_t* out, size_t cap, size_t* out_len)
+{
+    if (!meta || !filtered || !out || !out_len) return ICX_E_NULL;
+    if (meta->width <= 0 || meta->height <= 0 || meta->fmt < ICX_BGR24 || meta->fmt > ICX_BINARY1 || level < -1 ||
+        level > 9)
+        return ICX_E_INVALID;
+    if (icx::is_device_ptr(filtered)) return ICX_E_INVALID;  // host rows only
+    if (!palette_ok(meta)) return ICX_E_INVALID;
+    const size_t need = icx_png_bound(meta);
+    if (need == 0) return ICX_E_UNSUPPORTED;  // over kMaxRaw
+    if (len != icx_png_filtered_size(meta)) return ICX_E_INVALID;
+    *out_len = need;
+    if (cap < need) return ICX_E_BUFFER;
+    const bool pal = meta->fmt == ICX_INDEXED8 || meta->fmt == ICX_BINARY1;
+    const PalOut po = pal ? pal_out(meta) : PalOut{};
+    const int bpp = pal && po.ctype == 4 ? 2 : png_bpp(meta->fmt);
+    const size_t n = png_row_bytes(meta);
+    PngWriter w{out, cap};
+    w.header(meta, pal, po, bpp);
+    if (!w.begin(level)) return ICX_E_NOMEM;
+    for (int y = 0; y < meta->height; y++)
+        if (!w.row(filtered + (size_t)y * (n + 1), n + 1, y + 1 == meta->height)) break;
+    return w.end(out_len);
 }
 
 }  // extern "C"

@@ -49,6 +49,7 @@ std::vector<std::vector<int>> shares(const std::vector<double>& weight, int ndev
 bool host_only(const icx_fit_job& j) { return !icx::is_device_ptr(j.img.px) && !icx::is_device_ptr(j.out); }
 bool host_only(const icx_decode_job& j) { return !icx::is_device_ptr(j.data) && !icx::is_device_ptr(j.out); }
 bool host_only(const icx_png_fit_job& j) { return !icx::is_device_ptr(j.src.px) && !icx::is_device_ptr(j.dst); }
+bool host_only(const icx_png_fit_filter_job& j) { return !icx::is_device_ptr(j.src.px) && !icx::is_device_ptr(j.out); }
 
 // Runs fn(ctx, jobs, n) on every device's share of `jobs` in parallel.
 template <class Job, class Fn>
@@ -146,6 +147,15 @@ icx_status icx_pool_png_fit_batch(icx_pool* pool, icx_png_fit_job* jobs, int32_t
     std::vector<double> w(n);
     for (int i = 0; i < n; i++) w[i] = (double)jobs[i].src.width * jobs[i].src.height;
     return run_shares(pool, jobs, n, w, icx_png_fit_batch);
+}
+
+icx_status icx_pool_png_fit_filter_batch(icx_pool* pool, icx_png_fit_filter_job* jobs, int32_t n)
+{
+    if (!pool || (!jobs && n > 0)) return ICX_E_NULL;
+    if (n < 0) return ICX_E_INVALID;
+    std::vector<double> w(n);
+    for (int i = 0; i < n; i++) w[i] = (double)jobs[i].src.width * jobs[i].src.height;
+    return run_shares(pool, jobs, n, w, icx_png_fit_filter_batch);
 }
 
 }  // extern "C"

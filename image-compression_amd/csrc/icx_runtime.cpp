@@ -22,12 +22,14 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/icx.h"
 #include "icx_context.h"
 #include "icx_internal.h"
 #include "icx_kernels.h"
+#include "icx_pngfilter.h"
 
 using namespace icx;
 
@@ -1645,18 +1647,63 @@ icx_status icx_png_fit(icx_ctx* ctx, const icx_image* src, int32_t min_width, in
     return s;
 }
 
-icx_status icx_png_fit_batch(icx_ctx* ctx, icx_png_fit_job* jobs, int32_t n)
+}  // extern "C"
+
+namespace {
+
+uint8_t*& dst_of(icx_png_fit_job& j) { return j.dst; }
+uint8_t*& dst_of(icx_png_fit_filter_job& j) { return j.out; }
+void set_len(icx_png_fit_job&, size_t) {}
+void set_len(icx_png_fit_filter_job& j, size_t v) { j.out_len = v; }
+
+// The raster ImageTools.resizeImage returns for `src` at dw x dh: the
+// source's type, a palette type with its default colour map (pal: 256 entries).
+icx_image resized_meta(const icx_image& src, int dw, int dh, uint32_t* pal)
 {
+    icx_image r{};
+    r.width = dw;
+    r.height = dh;
+    r.fmt = src.fmt;
+    r.stride = dw * channels(src.fmt);
+    if (is_palette(src.fmt)) {
+        r.palette_len = default_palette(src.fmt == ICX_BINARY1, pal);
+        r.palette = pal;
+    }
+    return r;
+}
+
+// Device copy of a raster's colour map for the filter kernel (only the
+// grey + alpha rows read it), padded to 256 entries.
+hipError_t filter_palette(icx_ctx* c, const icx_image& img, PngFilterArgs& a, std::vector<std::vector<uint32_t>>& keep)
+{
+    a.pal = nullptr;
+    if (a.mode != PF_PAL_GA) return hipSuccess;
+    keep.emplace_back(256, 0u);
+    for (int i = 0; i < img.palette_len; i++) keep.back()[i] = img.palette[i];
+    uint32_t* dp = (uint32_t*)c->dev.take(1024);
+    a.pal = dp;
+    return hipMemcpyAsync(dp, keep.back().data(), 1024, hipMemcpyHostToDevice, c->stream);
+}
+
+// icx_png_fit_batch, and with FILTER its fused form: the resized frames stay
+// in the workspace, the filter kernel reads them there and only the filtered
+// streams leave.
+template <class Job>
+icx_status png_fit_impl(icx_ctx* ctx, Job* jobs, int32_t n)
+{
+    constexpr bool FILTER = std::is_same<Job, icx_png_fit_filter_job>::value;
     if (!ctx || (!jobs && n > 0)) return ICX_E_NULL;
     if (n < 0) return ICX_E_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     hipSetDevice(ctx->device);
     // ImageCompressionPng.java:45-66: the box test and scale per image
     std::vector<int> todo;
+    std::vector<size_t> flen(FILTER ? n : 0, 0);  // filtered stream bytes
     for (int i = 0; i < n; i++) {
-        icx_png_fit_job& j = jobs[i];
+        Job& j = jobs[i];
         j.resized = 0;
         j.out_w = j.out_h = 0;
+        set_len(j, 0);
         j.status = validate(&j.src);
         if (j.status) continue;
         if (j.src.width <= j.min_width && j.src.height <= j.min_height) {  // :49-53, the reference returns false
@@ -1664,7 +1711,7 @@ icx_status icx_png_fit_batch(icx_ctx* ctx, icx_png_fit_job* jobs, int32_t n)
             j.out_h = j.src.height;
             continue;
         }
-        if (!j.dst) {  // needed only for an image that is resized
+        if (!dst_of(j)) {  // needed only for an image that is resized
             j.status = ICX_E_NULL;
             continue;
         }
@@ -1674,7 +1721,18 @@ icx_status icx_png_fit_batch(icx_ctx* ctx, icx_png_fit_job* jobs, int32_t n)
             continue;
         }
         icx_scaled_dims(j.src.width, j.src.height, scale, &j.out_w, &j.out_h);  // ImageTools.java:8-9
-        if (j.cap < (size_t)j.out_w * j.out_h * channels(j.src.fmt)) {
+        size_t want = (size_t)j.out_w * j.out_h * channels(j.src.fmt);
+        if (FILTER) {
+            uint32_t pal[256];
+            const icx_image r = resized_meta(j.src, j.out_w, j.out_h, pal);
+            want = flen[i] = icx_png_filtered_size(&r);
+            set_len(j, want);
+            if (want == 0) {
+                j.status = ICX_E_UNSUPPORTED;
+                continue;
+            }
+        }
+        if (j.cap < want) {
             j.status = ICX_E_BUFFER;
             continue;
         }
@@ -1688,11 +1746,16 @@ icx_status icx_png_fit_batch(icx_ctx* ctx, icx_png_fit_job* jobs, int32_t n)
         std::vector<int> grp;
         size_t need = 1 << 20;
         while (pos < todo.size() && jobs[todo[pos]].src.fmt == fmt) {
-            const icx_png_fit_job& j = jobs[todo[pos]];
+            Job& j = jobs[todo[pos]];
             const size_t nch = channels(fmt);
             size_t per = 4096 + 2048;
             if (!is_device_ptr(j.src.px)) per += (size_t)j.src.width * j.src.height * nch + 256;
-            if (!is_device_ptr(j.dst)) per += (size_t)j.out_w * j.out_h * nch + 256;
+            if (FILTER) {
+                per += (size_t)j.out_w * j.out_h * nch + 256 + sizeof(PngFilterArgs) + 8 + 1024 + 256;
+                if (!is_device_ptr(dst_of(j))) per += flen[todo[pos]] + 256;
+            } else if (!is_device_ptr(dst_of(j))) {
+                per += (size_t)j.out_w * j.out_h * nch + 256;
+            }
             if (!grp.empty() && need + per > ctx->budget) break;
             need += per;
             grp.push_back(todo[pos++]);
@@ -1711,7 +1774,7 @@ icx_status icx_png_fit_batch(icx_ctx* ctx, icx_png_fit_job* jobs, int32_t n)
         std::vector<uint8_t*> dl(m, nullptr);  // device staging of host destinations
         int64_t dpx = 0, algo = 0, uniform = -1;
         for (int k = 0; k < m && e == hipSuccess; k++) {
-            const icx_png_fit_job& j = jobs[grp[k]];
+            Job& j = jobs[grp[k]];
             const int nch = channels(fmt);
             const uint8_t* sp = j.src.px;
             int sstride = j.src.stride;
@@ -1722,8 +1785,9 @@ icx_status icx_png_fit_batch(icx_ctx* ctx, icx_png_fit_job* jobs, int32_t n)
                 sp = st;
                 sstride = (int)row;
             }
-            uint8_t* dp = j.dst;
-            if (!is_device_ptr(dp)) dp = dl[k] = (uint8_t*)ctx->dev.take((size_t)j.out_w * j.out_h * nch);
+            uint8_t* dp = dst_of(j);
+            if (FILTER) dp = (uint8_t*)ctx->dev.take((size_t)j.out_w * j.out_h * nch);  // the frame stays here
+            else if (!is_device_ptr(dp)) dp = dl[k] = (uint8_t*)ctx->dev.take((size_t)j.out_w * j.out_h * nch);
             args[k] = resize_args(sp, j.src.width, j.src.height, sstride, fmt, dp, j.out_w, j.out_h, j.out_w * nch);
             if (e == hipSuccess) e = palette_args(ctx, j.src, args[k]);
             const int64_t tiles = resize_tiles(j.out_w, j.out_h);
@@ -1745,19 +1809,172 @@ icx_status icx_png_fit_batch(icx_ctx* ctx, icx_png_fit_job* jobs, int32_t n)
             Timed tm(ctx, "resize", dpx, true);
             launch_resize_batch(fmt, d_args, d_prefix, m, prefix[m], uniform > 0 ? uniform : 0, ctx->stream);
         }
+        // FILTER: the filter kernel over the group's frames, one launch
+        std::vector<PngFilterArgs> fargs(FILTER ? m : 0);
+        std::vector<int64_t> rows(FILTER ? m + 1 : 0, 0);
+        std::vector<std::vector<uint32_t>> keep;
+        if (FILTER) {
+            int64_t bytes = 0;
+            for (int k = 0; k < m && e == hipSuccess; k++) {
+                Job& j = jobs[grp[k]];
+                uint32_t pal[256];
+                const icx_image r = resized_meta(j.src, j.out_w, j.out_h, pal);
+                PngFilterArgs& a = fargs[k];
+                png_filter_desc(&r, &a);
+                a.src = args[k].dst;
+                a.sstride = r.stride;
+                a.out = dst_of(j);
+                if (!is_device_ptr(a.out)) a.out = dl[k] = (uint8_t*)ctx->dev.take(flen[grp[k]]);
+                e = filter_palette(ctx, r, a, keep);
+                rows[k + 1] = rows[k] + j.out_h;
+                bytes += (int64_t)flen[grp[k]];
+            }
+            PngFilterArgs* d_f = (PngFilterArgs*)ctx->dev.take(sizeof(PngFilterArgs) * m);
+            int64_t* d_rows = (int64_t*)ctx->dev.take(sizeof(int64_t) * (m + 1));
+            if (ctx->dev.overflow && e == hipSuccess) e = hipErrorOutOfMemory;
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(d_f, fargs.data(), sizeof(PngFilterArgs) * m, hipMemcpyHostToDevice, ctx->stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(d_rows, rows.data(), sizeof(int64_t) * (m + 1), hipMemcpyHostToDevice, ctx->stream);
+            if (e == hipSuccess) {
+                Timed tm(ctx, "pngfilter", bytes, true);
+                launch_png_filter(d_f, d_rows, m, rows[m], ctx->stream);
+            }
+        }
         for (int k = 0; k < m && e == hipSuccess; k++) {
             if (!dl[k]) continue;
-            const icx_png_fit_job& j = jobs[grp[k]];
-            e = hipMemcpyAsync(j.dst, dl[k], (size_t)j.out_w * j.out_h * channels(fmt), hipMemcpyDeviceToHost,
-                               ctx->stream);
+            Job& j = jobs[grp[k]];
+            const size_t len = FILTER ? flen[grp[k]] : (size_t)j.out_w * j.out_h * channels(fmt);
+            e = hipMemcpyAsync(dst_of(j), dl[k], len, hipMemcpyDeviceToHost, ctx->stream);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess) e = hipGetLastError();
         if (e != hipSuccess) {
             for (int i : grp) jobs[i].status = ICX_E_DEVICE;
-            return hip_fail(ctx, e, "png fit batch");
+            return hip_fail(ctx, e, FILTER ? "png fit + filter batch" : "png fit batch");
         }
         for (int i : grp) jobs[i].resized = 1;
+    }
+    resolve_profile(ctx);
+    return ICX_OK;
+}
+
+// What icx_png_encode checks of a raster before it writes.
+icx_status filter_check(const icx_image* img)
+{
+    if (!img->px) return ICX_E_NULL;
+    if (img->width <= 0 || img->height <= 0 || img->fmt < ICX_BGR24 || img->fmt > ICX_BINARY1 ||
+        (int64_t)img->stride < (int64_t)img->width * channels(img->fmt))
+        return ICX_E_INVALID;
+    if (is_palette(img->fmt) && (!img->palette || img->palette_len < 1 ||
+                                 img->palette_len > (img->fmt == ICX_BINARY1 ? 16 : 256)))
+        return ICX_E_INVALID;
+    return icx_png_bound(img) ? ICX_OK : ICX_E_UNSUPPORTED;  // over 1 GiB of rows
+}
+
+}  // namespace
+
+extern "C" {
+
+icx_status icx_png_fit_batch(icx_ctx* ctx, icx_png_fit_job* jobs, int32_t n) { return png_fit_impl(ctx, jobs, n); }
+
+icx_status icx_png_fit_filter_batch(icx_ctx* ctx, icx_png_fit_filter_job* jobs, int32_t n)
+{
+    return png_fit_impl(ctx, jobs, n);
+}
+
+icx_status icx_png_filter_batch(icx_ctx* ctx, icx_png_filter_job* jobs, int32_t n)
+{
+    if (!ctx || (!jobs && n > 0)) return ICX_E_NULL;
+    if (n < 0) return ICX_E_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    hipSetDevice(ctx->device);
+    std::vector<int> todo;
+    for (int i = 0; i < n; i++) {
+        icx_png_filter_job& j = jobs[i];
+        j.out_len = 0;
+        j.status = filter_check(&j.img);
+        if (j.status) continue;
+        if (!j.out) {
+            j.status = ICX_E_NULL;
+            continue;
+        }
+        j.out_len = icx_png_filtered_size(&j.img);
+        if (j.cap < j.out_len) {
+            j.status = ICX_E_BUFFER;
+            continue;
+        }
+        todo.push_back(i);
+    }
+    // in workspace-sized groups, formats and sizes mixed: one launch a group
+    size_t pos = 0;
+    while (pos < todo.size()) {
+        std::vector<int> grp;
+        size_t need = 1 << 20;
+        int64_t nrows = 0;
+        while (pos < todo.size()) {
+            const icx_png_filter_job& j = jobs[todo[pos]];
+            size_t per = 4096 + sizeof(PngFilterArgs) + 8 + 1024 + 256;
+            if (!is_device_ptr(j.img.px)) per += (size_t)j.img.width * channels(j.img.fmt) * j.img.height + 256;
+            if (!is_device_ptr(j.out)) per += j.out_len + 256;
+            if (!grp.empty() && (need + per > ctx->budget || nrows + j.img.height > 0x7fffffff)) break;
+            need += per;
+            nrows += j.img.height;
+            grp.push_back(todo[pos++]);
+        }
+        hipError_t e = ctx->dev.reserve(need + 4096);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            for (int i : grp) jobs[i].status = ICX_E_NOMEM;
+            continue;
+        }
+        ctx->dev.used = 0;
+        ctx->dev.overflow = false;
+        const int m = (int)grp.size();
+        std::vector<PngFilterArgs> fargs(m);
+        std::vector<int64_t> rows(m + 1, 0);
+        std::vector<uint8_t*> dl(m, nullptr);  // device staging of host destinations
+        std::vector<std::vector<uint32_t>> keep;
+        int64_t bytes = 0;
+        for (int k = 0; k < m && e == hipSuccess; k++) {
+            const icx_png_filter_job& j = jobs[grp[k]];
+            PngFilterArgs& a = fargs[k];
+            png_filter_desc(&j.img, &a);
+            a.src = j.img.px;
+            a.sstride = j.img.stride;
+            if (!is_device_ptr(a.src)) {
+                const size_t row = (size_t)j.img.width * channels(j.img.fmt);
+                uint8_t* st = (uint8_t*)ctx->dev.take(row * j.img.height);
+                e = hipMemcpy2DAsync(st, row, j.img.px, j.img.stride, row, j.img.height, hipMemcpyHostToDevice,
+                                     ctx->stream);
+                a.src = st;
+                a.sstride = (int)row;
+            }
+            a.out = j.out;
+            if (!is_device_ptr(a.out)) a.out = dl[k] = (uint8_t*)ctx->dev.take(j.out_len);
+            if (e == hipSuccess) e = filter_palette(ctx, j.img, a, keep);
+            rows[k + 1] = rows[k] + j.img.height;
+            bytes += (int64_t)j.out_len;
+        }
+        PngFilterArgs* d_f = (PngFilterArgs*)ctx->dev.take(sizeof(PngFilterArgs) * m);
+        int64_t* d_rows = (int64_t*)ctx->dev.take(sizeof(int64_t) * (m + 1));
+        if (ctx->dev.overflow && e == hipSuccess) e = hipErrorOutOfMemory;
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_f, fargs.data(), sizeof(PngFilterArgs) * m, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_rows, rows.data(), sizeof(int64_t) * (m + 1), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) {
+            Timed tm(ctx, "pngfilter", bytes, true);
+            launch_png_filter(d_f, d_rows, m, rows[m], ctx->stream);
+        }
+        for (int k = 0; k < m && e == hipSuccess; k++)
+            if (dl[k]) e = hipMemcpyAsync(jobs[grp[k]].out, dl[k], jobs[grp[k]].out_len, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) {
+            for (int i : grp) jobs[i].status = ICX_E_DEVICE;
+            return hip_fail(ctx, e, "png filter batch");
+        }
     }
     resolve_profile(ctx);
     return ICX_OK;

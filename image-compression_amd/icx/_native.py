@@ -34,6 +34,8 @@ EXPORTS = [
     "icx_debug_progressive_coefs", "icx_debug_recovery_coefs",
     "icx_device_alloc", "icx_device_free", "icx_memcpy", "icx_host_alloc", "icx_host_free",
     "icx_png_bound", "icx_png_encode", "icx_png_fit_batch",
+    "icx_png_filtered_size", "icx_png_filter_batch", "icx_png_fit_filter_batch", "icx_png_encode_filtered",
+    "icx_pool_png_fit_filter_batch",
     "icx_pool_create", "icx_pool_destroy", "icx_pool_size", "icx_pool_context", "icx_pool_compress_jpg_batch",
     "icx_pool_decode_jpg_batch", "icx_pool_png_fit_batch",
     "icx_device_count", "icx_debug_self_check_image", "icx_debug_corrupt_constants", "icx_upload",
@@ -85,6 +87,20 @@ class PngFitJob(ctypes.Structure):
                 ("dst", ctypes.c_void_p), ("cap", ctypes.c_size_t),
                 ("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32), ("resized", ctypes.c_int32),
                 ("status", ctypes.c_int32)]
+
+
+class PngFilterJob(ctypes.Structure):
+    """icx_png_filter_job (include/icx.h): one image of icx_png_filter_batch."""
+    _fields_ = [("img", Image), ("out", ctypes.c_void_p), ("cap", ctypes.c_size_t),
+                ("out_len", ctypes.c_size_t), ("status", ctypes.c_int32)]
+
+
+class PngFitFilterJob(ctypes.Structure):
+    """icx_png_fit_filter_job: icx_png_fit_job with the filtered stream as its output."""
+    _fields_ = [("src", Image), ("min_width", ctypes.c_int32), ("min_height", ctypes.c_int32),
+                ("out", ctypes.c_void_p), ("cap", ctypes.c_size_t),
+                ("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32), ("resized", ctypes.c_int32),
+                ("out_len", ctypes.c_size_t), ("status", ctypes.c_int32)]
 
 
 class StageJob(ctypes.Structure):
@@ -172,6 +188,12 @@ def load():
         "icx_png_bound": (c.c_size_t, [P(Image)]),
         "icx_png_encode": (c.c_int, [P(Image), c.c_int32, c.c_void_p, c.c_size_t, P(c.c_size_t)]),
         "icx_png_fit_batch": (c.c_int, [c.c_void_p, P(PngFitJob), c.c_int32]),
+        "icx_png_filtered_size": (c.c_size_t, [P(Image)]),
+        "icx_png_filter_batch": (c.c_int, [c.c_void_p, P(PngFilterJob), c.c_int32]),
+        "icx_png_fit_filter_batch": (c.c_int, [c.c_void_p, P(PngFitFilterJob), c.c_int32]),
+        "icx_pool_png_fit_filter_batch": (c.c_int, [c.c_void_p, P(PngFitFilterJob), c.c_int32]),
+        "icx_png_encode_filtered": (c.c_int, [P(Image), c.c_void_p, c.c_size_t, c.c_int32, c.c_void_p, c.c_size_t,
+                                              P(c.c_size_t)]),
         "icx_pool_create": (c.c_int, [P(c.c_int32), c.c_int32, P(c.c_void_p)]),
         "icx_pool_destroy": (None, [c.c_void_p]),
         "icx_pool_size": (c.c_int32, [c.c_void_p]),

@@ -58,6 +58,9 @@ def build_parser():
                         "larger calls measured no faster, DESIGN.md §9)")
     p.add_argument("--decode-threads", type=int, default=None)
     p.add_argument("--write-threads", type=int, default=4, help="threads writing the JPEG output files")
+    p.add_argument("--png-filter", choices=("device", "host"), default="device",
+                   help="where PNG rows are filtered: on the GPU behind the resize, or on the writer threads "
+                        "(the files are the same)")
     p.add_argument("-V", "--version", action="version", version="1.0")
     return p
 
@@ -101,7 +104,7 @@ def main(argv=None) -> int:
     codecs = [Codec(d) for d in devices for _ in range(max(1, a.workers_per_device))]
     batch = CompressionBatch(a.file_list, a.output_dir, params, a.timeOut, a.cache_db, codecs=codecs,
                              group_size=a.group, decode_threads=a.decode_threads, rank=rank, world=world,
-                             group_max=a.group_max, write_threads=a.write_threads)
+                             group_max=a.group_max, write_threads=a.write_threads, png_filter=a.png_filter)
     if dist is None:
         rep = batch.execute()
     else:

@@ -176,6 +176,25 @@ def _pixels(raster):
     return raster.indices if isinstance(raster, IndexedImage) else raster
 
 
+class FilteredPng:
+    """The filtered rows of one PNG image (icx_png_filter_batch /
+    icx_png_fit_filter_batch): `stream` holds height rows of 1 + row_bytes
+    (filter type, residuals) - a host uint8 array, or the DeviceImage it was
+    written to - with what the writer needs besides: width, height, fmt and,
+    for INDEXED8 / BINARY1, the colour map.  pngio.encode_png_filtered turns
+    it into the file encode_png writes for the pixels."""
+
+    def __init__(self, stream, width, height, fmt, palette=None):
+        self.stream, self.width, self.height, self.fmt, self.palette = stream, int(width), int(height), fmt, palette
+
+    def meta(self):
+        """(icx_image without pixels, the objects it points into)."""
+        pal = None if self.palette is None else np.ascontiguousarray(self.palette, dtype=np.uint32)
+        img = N.Image(None, self.width, self.height, self.width * N.BYTES_PER_PX[self.fmt], self.fmt,
+                      pal.ctypes.data if pal is not None else None, len(pal) if pal is not None else 0)
+        return img, pal
+
+
 class DeviceImage:
     """A frame (or byte string) in the codec GPU's HBM, allocated through the
     C ABI (icx_device_alloc): (H, W, 3) BGR or (H, W) grey uint8, contiguous.
@@ -544,6 +563,65 @@ class Codec:
             res.append(outs[i] if jobs[i].resized else None)
         return res
 
+    def png_filter_batch(self, images, fmts=None, outputs=None):
+        """The PNG writer's per-row filter for a group of images in one launch
+        (icx_png_filter_batch): images as png_fit_batch takes them, of any
+        formats and sizes.  Returns one FilteredPng per image; outputs[i], a
+        DeviceImage of at least the stream's bytes, keeps that stream in HBM."""
+        n = len(images)
+        jobs = (N.PngFilterJob * n)()
+        keep, res = [], []
+        for i, im in enumerate(images):
+            img, k = _image_struct(im, fmts[i] if fmts else None)
+            keep.append(k)
+            jobs[i].img = img
+            size = self._lib.icx_png_filtered_size(ctypes.byref(img))
+            out = outputs[i] if outputs is not None and outputs[i] is not None else np.empty(size, np.uint8)
+            jobs[i].out = out.data_ptr() if hasattr(out, "data_ptr") else out.ctypes.data
+            jobs[i].cap = out.numel() if hasattr(out, "numel") else out.nbytes
+            res.append(FilteredPng(out, img.width, img.height, img.fmt,
+                                   im.palette if isinstance(im, IndexedImage) else None))
+        with self._lock:
+            st = self._lib.icx_png_filter_batch(self._ctx, jobs, n)
+        self._check(st, "icx_png_filter_batch")
+        for i in range(n):
+            self._check(jobs[i].status, "icx_png_filter_batch job")
+        return res
+
+    def png_fit_filter_batch(self, images, params: CompressionParams, fmts=None):
+        """png_fit_batch with the PNG writer's row filter fused behind the
+        resize (icx_png_fit_filter_batch): per image None when it already
+        fits the box, else the FilteredPng of the resized image - the frame
+        itself stays on the device.  A resized INDEXED8 / BINARY1 image has
+        its type's default colour map, as png_fit_batch returns it."""
+        n = len(images)
+        jobs = (N.PngFitFilterJob * n)()
+        keep, outs = [], [None] * n
+        for i, im in enumerate(images):
+            img, k = _image_struct(im, fmts[i] if fmts else None)
+            keep.append(k)
+            j = jobs[i]
+            j.src = img
+            j.min_width, j.min_height = int(params.min_width), int(params.min_height)
+            if img.width <= params.min_width and img.height <= params.min_height:
+                continue
+            dw, dh = scaled_dims(img.width, img.height,
+                                 min(params.min_width / img.width, params.min_height / img.height))
+            pal = default_palette(img.fmt == N.BINARY1) if img.fmt in (N.INDEXED8, N.BINARY1) else None
+            f = FilteredPng(None, dw, dh, img.fmt, pal)
+            meta, mkeep = f.meta()
+            f.stream = np.empty(self._lib.icx_png_filtered_size(ctypes.byref(meta)), np.uint8)
+            outs[i] = f
+            j.out, j.cap = f.stream.ctypes.data, f.stream.nbytes
+        with self._lock:
+            st = self._batch_call("png_fit_filter", jobs, n)
+        self._check(st, "icx_png_fit_filter_batch")
+        res = []
+        for i in range(n):
+            self._check(jobs[i].status, "icx_png_fit_filter_batch job")
+            res.append(outs[i] if jobs[i].resized else None)
+        return res
+
     # -------------------------------------------------------------- A11 decode
     def decode_jpg_batch(self, datas, subsampling: int = 0, device_out: bool = False, infos=None):
         """Decode JPEG files (bytes / uint8 arrays / DeviceImage / CUDA uint8
@@ -654,7 +732,7 @@ class Codec:
 
 class Pool(Codec):
     """Several GPUs behind one libicx handle (icx_pool_*, include/icx.h): the
-    batched calls - fit, png_fit_batch, decode_jpg_batch - split the images
+    batched calls - fit, png_fit_batch, png_fit_filter_batch, decode_jpg_batch - split the images
     into per-device shares balanced by pixels, run them concurrently and
     return the results in the caller's order, as one Codec would.  Host
     buffers only (device_out / CUDA tensors belong with one device's Codec);

@@ -58,8 +58,8 @@ class StageTimes:
     pinned memory), parse (JPEG header), host_decode (Pillow: PNG and files
     the device decoder refuses), queue_wait (a GPU worker idle for work),
     gpu_decode / gpu_fit / gpu_png (the batched device calls, wall time of
-    the calling worker), write (JPEG file writes), png_write (filter + deflate
-    + write)."""
+    the calling worker), write (JPEG file writes), png_write (deflate + write;
+    with png_filter "host" the row filter too)."""
 
     def __init__(self):
         self._lock = threading.Lock()
@@ -722,10 +722,16 @@ def compress_jpeg_group(codec, items: List[_Item], params: CompressionParams, ca
 
 
 def _png_write(it: _Item, resized):
+    """Writes the PNG of a resized raster (filter + deflate here), or of the
+    FilteredPng the device filtered already (deflate and CRCs only)."""
     try:
-        from .pngio import write_png
+        from .core import FilteredPng
+        from .pngio import write_png, write_png_filtered
         with _span("png_write"):
-            write_png(it.output, resized)
+            if isinstance(resized, FilteredPng):
+                write_png_filtered(it.output, resized)
+            else:
+                write_png(it.output, resized)
         _finish(it, True)
     except Exception as e:
         _fail(it, e)
@@ -749,17 +755,23 @@ def compress_png_item(codec, it: _Item, params: CompressionParams, writer=None):
         _fail(it, e)
 
 
-def compress_png_group(codec, items: List[_Item], params: CompressionParams, writer=None):
+def compress_png_group(codec, items: List[_Item], params: CompressionParams, writer=None, png_filter="device"):
     """compressPngWithTargetSize for a group of PNGs: the resizes in one device
-    launch (icx_png_fit_batch), filter + deflate + file write per image on
-    `writer`.  A codec without the batched entry point takes them one by one."""
+    launch, deflate + file write per image on `writer`.  png_filter "device":
+    the rows are filtered on the device behind the resize
+    (icx_png_fit_filter_batch) and only the filtered streams come back;
+    "host" (or a codec without the fused call): the frames come back
+    (icx_png_fit_batch) and the writer threads filter them.  The files are the
+    same.  A codec without a batched entry point takes them one by one."""
     if writer is None or not hasattr(codec, "png_fit_batch"):
         for it in items:
             compress_png_item(codec, it, params, writer)
         return
+    fused = png_filter == "device" and hasattr(codec, "png_fit_filter_batch")
     try:
         with _span("gpu_png"):
-            res = codec.png_fit_batch([it.decoded.image for it in items], params)
+            res = (codec.png_fit_filter_batch if fused else codec.png_fit_batch)(
+                [it.decoded.image for it in items], params)
     except Exception:  # a bad image fails alone: redo the group one by one
         for it in items:
             compress_png_item(codec, it, params, writer)
@@ -970,7 +982,10 @@ class CompressionBatch:
                  h2_cache_path="image-compression-cache", codecs=None, group_size: int = 64,
                  decode_threads: Optional[int] = None, rank: int = 0, world: int = 1,
                  device_decode: Optional[bool] = None, stage_times: bool = False, group_max: int = 0,
-                 write_threads: int = 4):
+                 write_threads: int = 4, png_filter: str = "device"):
+        if png_filter not in ("device", "host"):
+            raise ValueError("png_filter: 'device' or 'host'")
+        self.png_filter = png_filter  # where the PNG rows are filtered (--png-filter)
         self.file_list_path = file_list_path
         self.save_dir = save_dir
         self.params = params
@@ -1107,7 +1122,7 @@ class CompressionBatch:
             if kind == "jpeg":
                 compress_jpeg_group(codec, its, self.params, cache, jpeg_writer)
             elif kind == "png":
-                compress_png_group(codec, its, self.params, writer)
+                compress_png_group(codec, its, self.params, writer, self.png_filter)
             else:
                 for it in its:
                     compress_image_iteratively(codec, it, self.params, cache)

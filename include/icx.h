@@ -302,6 +302,59 @@ icx_status icx_pool_png_fit_batch(icx_pool* pool, icx_png_fit_job* jobs, int32_t
 size_t icx_png_bound(const icx_image* img);
 icx_status icx_png_encode(const icx_image* img, int32_t level, uint8_t* out, size_t cap, size_t* out_len);
 
+/* The row filter of icx_png_encode on the device, and the rest of the writer
+ * on the host.  The filtered stream of an image is what icx_png_encode hands
+ * to deflate: height rows of 1 + row_bytes, the filter type then the
+ * residuals (palette images: type 0 and the packed indices), rows in PNG
+ * sample order.  icx_png_filtered_size = height * (row_bytes + 1), 0 where
+ * icx_png_bound is 0.
+ * icx_png_filter_batch filters a group of images (any formats and sizes,
+ * host or device pixels, every raster icx_png_encode accepts) in one launch
+ * into `out` (host or device, cap >= icx_png_filtered_size).  Per-job
+ * out_len / status are filled in (ICX_E_NULL, ICX_E_INVALID, ICX_E_BUFFER
+ * with out_len = needed bytes); returns ICX_OK unless a context-level failure
+ * occurred. */
+size_t icx_png_filtered_size(const icx_image* img);
+typedef struct icx_png_filter_job {
+    /* inputs */
+    icx_image img; /* host or device pixels */
+    uint8_t* out;  /* host or device */
+    size_t cap;
+    /* outputs */
+    size_t out_len;
+    icx_status status;
+} icx_png_filter_job;
+icx_status icx_png_filter_batch(icx_ctx* ctx, icx_png_filter_job* jobs, int32_t n);
+
+/* icx_png_fit_batch and the filter fused: the box test and scale exactly as
+ * icx_png_fit_batch; the resized frame stays in the context's workspace and
+ * only its filtered stream is written to `out` (the resized raster keeps the
+ * source's type; a palette type gets its default colour map,
+ * icx_default_palette).  A job whose image already fits the box gets
+ * resized = 0 and nothing written. */
+typedef struct icx_png_fit_filter_job {
+    /* inputs */
+    icx_image src;
+    int32_t min_width, min_height;
+    uint8_t* out; /* host or device; may be NULL for an image that already fits the box */
+    size_t cap;
+    /* outputs */
+    int32_t out_w, out_h;
+    int32_t resized;
+    size_t out_len; /* filtered stream bytes (with ICX_E_BUFFER: the bytes needed) */
+    icx_status status;
+} icx_png_fit_filter_job;
+icx_status icx_png_fit_filter_batch(icx_ctx* ctx, icx_png_fit_filter_job* jobs, int32_t n);
+icx_status icx_pool_png_fit_filter_batch(icx_pool* pool, icx_png_fit_filter_job* jobs, int32_t n);
+
+/* Host only: the PNG file of a filtered stream.  meta gives width, height,
+ * fmt and palette (px and stride are ignored); the file is the one
+ * icx_png_encode writes for the pixels that produced `filtered` (same header,
+ * same deflate calls, same IDAT cut).  len != icx_png_filtered_size(meta)
+ * returns ICX_E_INVALID; needs cap >= icx_png_bound(meta). */
+icx_status icx_png_encode_filtered(const icx_image* meta, const uint8_t* filtered, size_t len, int32_t level,
+                                   uint8_t* out, size_t cap, size_t* out_len);
+
 /* ------------------------------------------------------------- decode (A11) */
 /* ImageCompression.decodeImageWithSubsampling (ImageCompression.java:107-165)
  * for JPEG: the JDK JPEGImageReader (IJG 6b: ISLOW IDCT, fancy upsampling,
@@ -417,7 +470,8 @@ icx_status icx_debug_fdct(icx_ctx* ctx, const icx_image* img, int16_t* coefs, si
 
 /* Per-kernel timing with HIP events recorded on the context's stream around
  * every launch of the named kernel ("fdct", "huff", "scan", "ffcount",
- * "decide", "stuff", "resize").  Enabling adds one event pair per launch. */
+ * "decide", "stuff", "resize", "pngfilter": units = filtered stream bytes).
+ * Enabling adds one event pair per launch. */
 icx_status icx_profile_enable(icx_ctx* ctx, int32_t on);
 icx_status icx_profile_reset(icx_ctx* ctx);
 icx_status icx_profile_query(icx_ctx* ctx, const char* kernel, int64_t* launches, double* total_ms,

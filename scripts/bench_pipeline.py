@@ -51,6 +51,8 @@ def main():
     ap.add_argument("--procs", type=int, default=1, help="processes sharing the list (warm-cache run only)")
     ap.add_argument("--decode-threads", type=int, default=0, help="host reader threads (0: every usable core)")
     ap.add_argument("--write-threads", type=int, default=4, help="JPEG output writer threads (the CLI default)")
+    ap.add_argument("--png-filter", choices=("device", "host"), default="device",
+                    help="where the PNG rows are filtered (the CLI's --png-filter)")
     a = ap.parse_args()
     from PIL import Image
 
@@ -98,7 +100,7 @@ def main():
         return
     codecs = [icx.Codec(int(d)) for d in a.devices.split(",")]
     kernels = ("dec_unstuff", "dec_init", "dec_sync", "dec_sync_r1", "dec_sync_r2", "dec_sync_r3", "dec_write",
-               "dec_dc", "dec_idct", "dec_color", "fdct", "huff", "scan", "ffscan", "stuff", "resize")
+               "dec_dc", "dec_idct", "dec_color", "fdct", "huff", "scan", "ffscan", "stuff", "resize", "pngfilter")
     from icx.cache import LockedDict
 
     class NoHits(LockedDict):  # a learned cache that never hits: every file searches
@@ -108,7 +110,8 @@ def main():
     def batch(out, cache_db):
         return pipeline.CompressionBatch(lst, out, params, 1, cache_db, codecs=codecs, group_size=a.group,
                                          decode_threads=a.decode_threads or None, stage_times=True,
-                                         group_max=a.group_max, write_threads=a.write_threads)
+                                         group_max=a.group_max, write_threads=a.write_threads,
+                                         png_filter=a.png_filter)
     if not a.no_warmup:  # untimed: the process's first-use costs (its own cache DB)
         batch(os.path.join(work, "out_w"), os.path.join(work, "cache_w")).execute()
         shutil.rmtree(os.path.join(work, "out_w"), ignore_errors=True)
@@ -168,7 +171,7 @@ def main():
     print(json.dumps({"metric": "CompressionBatch end-to-end (files -> files), 4K q95 JPEG" +
                                 (" + 4K PNG (configs[4] mix)" if a.png else "") + ", -t 1MiB, devices " + a.devices,
                       "files": a.files, "png_files": a.png, "group_size": a.group, "group_max": a.group_max,
-                      "write_threads": a.write_threads,
+                      "write_threads": a.write_threads, "png_filter": a.png_filter,
                       "mean_src_bytes": int(np.mean([len(b) for b in blobs])),
                       "mean_png_src_bytes": int(np.mean([len(b) for b in png_blobs])) if png_blobs else 0,
                       "summary": summary, "runs": runs}))
