@@ -197,6 +197,10 @@ struct icx_ctx {
     std::map<std::string, icx::KStat> stats;
     size_t budget = 0;  // device workspace budget per sub-batch
     int table_layout = 0;  // ICX_TABLES_SEPARATE / ICX_TABLES_GROUPED (icx_set_table_layout)
+    // probe bound: on unless ICX_PROBE_BOUND=0 at creation;
+    // (dcmin, acmin) of a grey and of a colour image, from the coding tables
+    bool probe_bound = true;
+    int32_t bound_mins[4] = {0, 0, 0, 0};
     // inverse colour maps of the default TYPE_BYTE_INDEXED [0] / TYPE_BYTE_BINARY
     // [1] maps (32x32x32, device), built at the first palette resize
     uint8_t* d_inv[2] = {nullptr, nullptr};

@@ -101,7 +101,26 @@ struct ImgDesc {
     uint32_t* ovf;            // per-block spill of Huffman words beyond the LDS slot
     uint8_t* out;
     uint64_t cap;
+    // QNode of the cached probe when probe_bound() may decide that probe
+    // without a trial (the candidate filter is the probe's own thresholds, so
+    // every AC list entry is nonzero at the probe's quality), else -1
+    int32_t bound_node;
+    int32_t pad;
 };
+
+// Lower bound of a JPEG file's size from the candidate-list lengths of an
+// image whose list filter is the coded quality's own threshold set: every AC
+// entry of every list then quantises to nonzero and costs at least acmin bits
+// (shortest AC code + one magnitude bit), every block's DC at least dcmin
+// bits (shortest DC code + its size); zero runs, EOB and 0xFF stuffing cost at
+// least nothing.  ncoef_sum: sum of the true list lengths, DC included (no
+// padding).  Header + EOI + the entropy bytes of that many bits.
+__host__ __device__ inline int64_t probe_bound(int32_t hdr_len, int64_t nblocks, int64_t ncoef_sum, int32_t dcmin,
+                                               int32_t acmin)
+{
+    const int64_t bits = (int64_t)dcmin * nblocks + (int64_t)acmin * (ncoef_sum - nblocks);
+    return (int64_t)hdr_len + 2 + (bits + 7) / 8;
+}
 
 constexpr int ENT_SLOTS = 16;
 
@@ -125,7 +144,9 @@ struct ImgState {
     // (at least total_bits / 8) and its per-chunk bit counts and 0xFF bins
     uint64_t huff_wbytes;
     float trial_q[MAX_TRIALS + 1];
-    int64_t trial_size[MAX_TRIALS + 1];
+    int64_t trial_size[MAX_TRIALS + 1];  // -1: decided "too big" by probe_bound, not coded
+    int32_t nbounded;      // trials of ntrials that probe_bound decided (k_list_count)
+    int32_t pad;
 };
 
 // A launch plan: the images taking part (ids into desc/state arrays) and

@@ -835,7 +835,8 @@ __device__ __forceinline__ uint32_t fdct_compute(const FdctTile& T, const uint32
 }
 
 // The FDCT keeps no count of the list entries it writes: the byte
-// accounting (profiling only) gets them from k_list_count.  A global atomic
+// accounting (profiling only) and the probe bound get them from
+// k_list_count.  A global atomic
 // per wave and tile (16 counters per image) cost 5.7 % of the FDCT time, one
 // per workgroup still 4.3 % (profiles/r3/ab_r3zg_fdct_lds.txt,
 // ab_r3zh_fdct_ent.txt): a wave whose last instruction is a device-scope
@@ -979,32 +980,77 @@ __global__ __launch_bounds__(256) void k_fdct_gray(const ImgDesc* __restrict__ d
 // of the list length padded to whole 16-B groups, as emit_lists lays them
 // out.  One workgroup per image; lengths 16 at a time ((n + 3) & ~3 per byte
 // without carries: every length is <= 64), summed by v_dot4_u32_u8.
+//
+// The same pass takes the probe bound (bound != 0): for an
+// image whose pending trial is the cached probe D.bound_node, the true list
+// lengths give probe_bound(), a lower bound of that trial's file size.  Above
+// the target, the trial's only possible outcome is "too big", so the search
+// step decide_trial would take after coding it is taken here and k_huff /
+// k_scan find the image inactive.  count: keep the padded entry count (the
+// profile's byte accounting).  mins: (dcmin, acmin) for grey and for colour
+// images, from the coding tables (icx_create).
 __global__ __launch_bounds__(1024) void k_list_count(const ImgDesc* __restrict__ descs, ImgState* states,
-                                                     const int32_t* __restrict__ ids, int m)
+                                                     const QNode* __restrict__ nodes,
+                                                     const int32_t* __restrict__ ids, int m, int count, int bound,
+                                                     int4 mins)
 {
-    __shared__ uint32_t s_w[16];
+    __shared__ uint32_t s_w[2][16];
     const int img = ids ? ids[blockIdx.x] : (int)blockIdx.x;
     const ImgDesc& D = descs[img];
+    ImgState& S = states[img];
+    // workgroup-uniform: only an image the bound may decide is summed when
+    // nothing is counted
+    const bool try_bound = bound && D.bound_node >= 0 && S.active && !S.force && S.node == D.bound_node;
+    if (!count && !try_bound) return;
     const int64_t n = D.nblocks;
     const uint8_t* nc = D.ncoef;
     const int64_t n16 = ((uintptr_t)nc & 15) ? 0 : n >> 4;
-    uint32_t sum = 0;
+    uint32_t sum = 0, len = 0;  // padded entries; true list lengths (<= 64 per block: < 2^32 for any image)
     for (int64_t i = threadIdx.x; i < n16; i += blockDim.x) {
         const uint4 v = ld16(nc + 16 * i);
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int k = 0; k < 4; k++)
+        for (int k = 0; k < 4; k++) {
             sum = __builtin_amdgcn_udot4((w[k] + 0x03030303u) & 0xFCFCFCFCu, 0x01010101u, sum, false);
+            len = __builtin_amdgcn_udot4(w[k], 0x01010101u, len, false);
+        }
     }
-    for (int64_t i = n16 * 16 + threadIdx.x; i < n; i += blockDim.x) sum += ((uint32_t)gp(nc)[i] + 3u) & ~3u;
+    for (int64_t i = n16 * 16 + threadIdx.x; i < n; i += blockDim.x) {
+        const uint32_t v = gp(nc)[i];
+        sum += (v + 3u) & ~3u;
+        len += v;
+    }
     sum = (uint32_t)wave_incl_scan((int)sum);
+    len = (uint32_t)wave_incl_scan((int)len);
     const int lane = threadIdx.x & 63;
-    if (lane == 63) s_w[threadIdx.x >> 6] = sum;
+    if (lane == 63) {
+        s_w[0][threadIdx.x >> 6] = sum;
+        s_w[1][threadIdx.x >> 6] = len;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        uint64_t tot = 0;
-        for (int i = 0; i < (int)(blockDim.x >> 6); i++) tot += s_w[i];
-        atomicAdd((unsigned long long*)states[img].list_entries, (unsigned long long)tot);
+        uint64_t tot = 0, lens = 0;
+        for (int i = 0; i < (int)(blockDim.x >> 6); i++) {
+            tot += s_w[0][i];
+            lens += s_w[1][i];
+        }
+        if (count) atomicAdd((unsigned long long*)S.list_entries, (unsigned long long)tot);
+        if (try_bound) {
+            const bool grey = D.ncomp == 1;
+            const int64_t low = probe_bound(D.hdr_len, n, (int64_t)lens, grey ? mins.x : mins.z, grey ? mins.y : mins.w);
+            if (low > D.target) {  // decide_trial's "too big" step; best_* and huff_wbytes untouched
+                const QNode& N = nodes[S.node];
+                if (S.ntrials <= MAX_TRIALS) {
+                    S.trial_q[S.ntrials] = N.mid;
+                    S.trial_size[S.ntrials] = -1;
+                }
+                S.ntrials++;
+                S.nbounded++;
+                const int next = N.child_nofit;
+                S.node = next;
+                S.active = next >= 0;
+            }
+        }
     }
 }
 
@@ -1256,16 +1302,28 @@ __global__ __launch_bounds__(HUFF_THREADS, ICX_HUFF_WGS) void k_huff(const ImgDe
     const int img = ids ? ids[slot] : slot;
     const ImgState& S = states[img];
     const ImgDesc& D = descs[img];
+    // An image with no trial pending (its search ended, or the probe bound
+    // decided its probe: k_list_count) leaves on the first wait: its state's
+    // flag comes in with the descriptor fields the prologue needs anyway
+    // (the empty asm keeps those loads in front of the exit: sunk behind it,
+    // each would be a wait of its own for the images still searching).
+    const int active = S.active;
+    const int64_t nblocks = D.nblocks;
+    const int ncomp = D.ncomp;
+    const GAS uint32_t* coff = gp(D.coff);
+    const GAS uint8_t* ncoef = gp(D.ncoef);
+    asm volatile("" ::"s"(nblocks), "s"(ncomp), "s"(coff), "s"(ncoef));
+    if (!active) return;
     const int chunk = gridDim.y > 1 ? (int)blockIdx.x : (int)(blockIdx.x - prefix[slot]);
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
 
     const int64_t b0 = (int64_t)chunk * CHUNK_BLOCKS;
-    const int nb = (int)min((int64_t)CHUNK_BLOCKS, D.nblocks - b0);
+    const int nb = (int)min((int64_t)CHUNK_BLOCKS, nblocks - b0);
     const bool valid = t < nb;
     const int64_t b = b0 + t;
     int tb = 0;
     int64_t pb;
-    if (D.ncomp == 3) {
+    if (ncomp == 3) {
         const uint32_t k6 = ((uint32_t)(chunk % 3) * 4u + (uint32_t)t) % 6u;  // b % 6, b0 = 256 chunk
         tb = k6 >= 4;
         if (k6 >= 1 && k6 <= 3) pb = b - 1;
@@ -1279,7 +1337,7 @@ __global__ __launch_bounds__(HUFF_THREADS, ICX_HUFF_WGS) void k_huff(const ImgDe
     // eight memory latencies in front of every chunk): first the block's
     // list length and offset, the DC predictor's list offset and the coding
     // tables (the list meta depends only on the descriptor, so it goes out
-    // even before the image's state says whether it is still searching);
+    // before the rest of the image's state - node, buffer - is waited for);
     // then, once the tables are in LDS, the list itself and the predictor's
     // DC entry (the list groups are loaded unconditionally, see load_group).
     // The DC predictor (the previous block of the same component: 1, 3 or 6
@@ -1290,11 +1348,9 @@ __global__ __launch_bounds__(HUFF_THREADS, ICX_HUFF_WGS) void k_huff(const ImgDe
     // own, and its DC quantised here.
     const bool in_wave = pb >= b0 && (int)(pb - b0) >= (t & ~63);
     const bool ext_prev = valid && pb >= 0 && !in_wave;  // (a lane past the chunk's blocks reads nothing)
-    const GAS uint32_t* coff = gp(D.coff);
-    const int cnt = valid ? (int)gp(D.ncoef)[b] : 0;
+    const int cnt = valid ? (int)ncoef[b] : 0;
     const uint32_t my_off = coff[valid ? b : b0];
     const uint32_t prev_off = coff[ext_prev ? pb : b0];
-    if (!S.active) return;
     const QNode& N = nodes[S.node];
     const int cur = S.cur;
     const float4 qv = N.qf[(t >> 6) & 1][t & 63];  // used by t < 128
@@ -2148,9 +2204,11 @@ void launch_fdct(const ImgDesc* d, ImgState* s, const QNode* n, const Plan& p, i
         ICX_LAUNCH(k_fdct_color<false>, grid, dim3(256), 0, st, d, n, s, plan_ids(p), p.prefix, p.m);
 }
 
-void launch_list_count(const ImgDesc* d, ImgState* s, const Plan& p, hipStream_t st)
+void launch_list_count(const ImgDesc* d, ImgState* s, const QNode* n, const Plan& p, bool count, bool bound,
+                       const int32_t mins[4], hipStream_t st)
 {
-    ICX_LAUNCH(k_list_count, dim3(p.m), dim3(1024), 0, st, d, s, plan_ids(p), p.m);
+    ICX_LAUNCH(k_list_count, dim3(p.m), dim3(1024), 0, st, d, s, n, plan_ids(p), p.m, count ? 1 : 0, bound ? 1 : 0,
+               make_int4(mins[0], mins[1], mins[2], mins[3]));
 }
 
 void launch_huff(const ImgDesc* d, const ImgState* s, const QNode* n, const Plan& p, int64_t wgs, bool rev,

@@ -456,15 +456,19 @@ void stage_pixels(Batch& B, int i, double scale)
     d.target = keep.target;
 }
 
-icx_status run_fdct(Batch& B, const std::vector<int>& ids)
+// probe: the FDCT of the cached-probe stage - the images whose descriptor
+// names a bound_node then get the probe bound's search step (k_list_count).
+icx_status run_fdct(Batch& B, const std::vector<int>& ids, bool probe = false)
 {
     for (int kind = 0; kind < 3; kind++) {
         std::vector<int> sel;
         std::vector<int64_t> cnt;
+        bool bound = false;
         for (int i : ids)
             if (B.it[i].kind == kind) {
                 sel.push_back(i);
                 cnt.push_back(fdct_tiles(B.desc[i]));
+                bound |= probe && B.desc[i].bound_node >= 0;
             }
         if (sel.empty()) continue;
         DPlan P;
@@ -477,9 +481,11 @@ icx_status run_fdct(Batch& B, const std::vector<int>& ids)
             Timed tm(B.c, "fdct", px, true);
             launch_fdct(B.d_desc, B.d_state, B.d_nodes, P.p, P.total, kind, B.c->stream);
         }
-        if (B.c->prof) {  // list sizes for the byte accounting (the FDCT keeps no count)
+        // list sizes: for the byte accounting (the FDCT keeps no count) and
+        // for the probe bound
+        if (B.c->prof || bound) {
             Timed tm(B.c, "count", (int64_t)sel.size(), true);
-            launch_list_count(B.d_desc, B.d_state, P.p, B.c->stream);
+            launch_list_count(B.d_desc, B.d_state, B.d_nodes, P.p, B.c->prof, bound, B.c->bound_mins, B.c->stream);
         }
     }
     return ICX_OK;
@@ -510,14 +516,17 @@ void credit_fdct(Batch& B, const std::vector<int>& ids)
 void credit_huff(Batch& B, const std::vector<int>& ids)
 {
     if (!B.c->prof) return;
-    int64_t blocks = 0, bytes = 0;
+    int64_t blocks = 0, bytes = 0, bounded = 0;
     for (int i : ids) {
-        blocks += (int64_t)B.state[i].ntrials * B.desc[i].nblocks;
-        bytes += (int64_t)B.state[i].ntrials * (4 * B.it[i].entries + 5 * B.desc[i].nblocks) +
-                 (int64_t)B.state[i].huff_wbytes;
+        // a trial the probe bound decided was not coded
+        const int64_t coded = B.state[i].ntrials - B.state[i].nbounded;
+        blocks += coded * B.desc[i].nblocks;
+        bytes += coded * (4 * B.it[i].entries + 5 * B.desc[i].nblocks) + (int64_t)B.state[i].huff_wbytes;
+        bounded += B.state[i].nbounded;
     }
     B.c->stats["huff"].units += blocks;
     B.c->stats["huff.bytes"].units += bytes;
+    B.c->stats["bound"].units += bounded;  // images decided by the probe bound
 }
 
 // `depth` trials (k_huff + k_scan with its search step) for the images in ids,
@@ -874,6 +883,15 @@ icx_status run_batch(icx_ctx* c, icx_fit_job* jobs, int n, Mode mode, int16_t* f
             }
             B.desc[k].cand_node = f->second;
             I.orig.cand_node = f->second;
+            // Probe bound: valid when the lists are filtered by the cached
+            // probe's own thresholds (no tree node reaches below them: every
+            // AC entry then quantises to nonzero at the probe's quality), in a
+            // fit (the probe is not forced).
+            bool bound = c->probe_bound && mode == Mode::Fit && I.cached_node >= 0;
+            for (int cc = 0; cc < 2 && bound; cc++)
+                for (int z = 1; z < 64 && bound; z++)
+                    bound = B.nodes[f->second].qf[cc][z].x == B.nodes[I.cached_node].qf[cc][z].x;
+            B.desc[k].bound_node = I.orig.bound_node = bound ? I.cached_node : -1;
         }
         B.d_nodes = (QNode*)c->dev.take(sizeof(QNode) * B.nodes.size());
         B.h_state = (ImgState*)c->host.take(sizeof(ImgState) * m);
@@ -942,7 +960,7 @@ icx_status run_batch(icx_ctx* c, icx_fit_job* jobs, int n, Mode mode, int16_t* f
                     init_state(B.state[k], B.it[k].cached_node, false);
                     B.it[k].coef_scale = sc < 1.0 ? sc : 1.0;
                 }
-                if ((s = push_desc_state(B)) || (s = run_fdct(B, probe)) || (s = run_trials(B, probe, 1, true)) ||
+                if ((s = push_desc_state(B)) || (s = run_fdct(B, probe, true)) || (s = run_trials(B, probe, 1, true)) ||
                     (s = sync_states(B)))
                     return s;
                 credit_fdct(B, probe);
@@ -1204,6 +1222,37 @@ const Consts& consts()
     });
     return K;
 }
+
+// probe_bound's per-symbol minima from the tables the encoder codes with:
+// dcmin = the cheapest DC difference (code length + size bits), acmin = the
+// cheapest nonzero AC coefficient (code length of a (run, size >= 1) symbol +
+// size bits); [0..1] over the luminance tables (a grey image), [2..3] over
+// both (a colour image).
+void bound_minima(const Consts& K, int32_t out[4])
+{
+    int dcm[2], acm[2];
+    for (int c = 0; c < 2; c++) {
+        dcm[c] = acm[c] = INT32_MAX;
+        for (int s = 0; s < 16; s++) {
+            const int len = (int)(K.dc[c][s] & 255);
+            if (len) dcm[c] = std::min(dcm[c], len + s);
+        }
+        for (int sym = 0; sym < 256; sym++) {
+            const int len = (int)(K.ac[c][sym] & 255), s = sym & 15;
+            if (len && s) acm[c] = std::min(acm[c], len + s);
+        }
+    }
+    out[0] = dcm[0];
+    out[1] = acm[0];
+    out[2] = std::min(dcm[0], dcm[1]);
+    out[3] = std::min(acm[0], acm[1]);
+}
+
+bool probe_bound_off()
+{
+    const char* e = getenv("ICX_PROBE_BOUND");
+    return e && atoi(e) == 0;
+}
 }  // namespace
 
 extern "C" {
@@ -1280,6 +1329,8 @@ icx_status icx_create(int device, icx_ctx** out)
     static std::mutex up_mu;
     static std::vector<int> up_done;
     const Consts& K = consts();
+    c->probe_bound = !probe_bound_off();
+    bound_minima(K, c->bound_mins);
     hipError_t up = hipSuccess;
     {
         std::lock_guard<std::mutex> lk(up_mu);
@@ -1452,6 +1503,19 @@ int64_t icx_num_blocks(int32_t width, int32_t height, int32_t fmt)
     ImgDesc d{};
     geometry(d, width, height, fmt);
     return d.nblocks;
+}
+
+int64_t icx_debug_probe_bound(int32_t width, int32_t height, int32_t fmt, int32_t layout, int64_t ncoef_sum)
+{
+    if (width <= 0 || height <= 0 || fmt < ICX_BGR24 || fmt > ICX_GRAY8) return -1;
+    if (layout != ICX_TABLES_SEPARATE && layout != ICX_TABLES_GROUPED) return -1;
+    ImgDesc d{};
+    geometry(d, width, height, fmt, layout);
+    if (ncoef_sum < d.nblocks || ncoef_sum > d.nblocks * 64) return -1;
+    int32_t mins[4];
+    bound_minima(consts(), mins);
+    const int g = d.ncomp == 1 ? 0 : 2;
+    return probe_bound(d.hdr_len, d.nblocks, ncoef_sum, mins[g], mins[g + 1]);
 }
 
 icx_status icx_compress_jpg_to_stream(icx_ctx* ctx, const icx_image* img, float quality, uint8_t* out, size_t cap,

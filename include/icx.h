@@ -468,9 +468,23 @@ icx_status icx_debug_recovery_coefs(const uint8_t* data, size_t len, int16_t* co
 int64_t icx_num_blocks(int32_t width, int32_t height, int32_t fmt);
 icx_status icx_debug_fdct(icx_ctx* ctx, const icx_image* img, int16_t* coefs, size_t ncoefs);
 
+/* Host-only: the probe bound, the lower bound of a file's size the fit takes
+ * from an image's candidate lists to decide a cached probe "too big" without
+ * coding it (ICX_PROBE_BOUND=0 at icx_create turns that off).  For a width x
+ * height image of `fmt` (BGR24 / RGB24 / GRAY8) written with table `layout`,
+ * whose lists hold ncoef_sum entries in all - per block the DC plus every AC
+ * coefficient that quantises to nonzero at the coded quality:
+ *   header + 2 + ceil((dcmin * nblocks + acmin * (ncoef_sum - nblocks)) / 8)
+ * with dcmin / acmin the cheapest DC difference / nonzero AC coefficient of
+ * the encoder's Huffman tables (code + magnitude bits).  -1 for arguments out
+ * of range; no context and no GPU needed. */
+int64_t icx_debug_probe_bound(int32_t width, int32_t height, int32_t fmt, int32_t layout, int64_t ncoef_sum);
+
 /* Per-kernel timing with HIP events recorded on the context's stream around
  * every launch of the named kernel ("fdct", "huff", "scan", "ffcount",
- * "decide", "stuff", "resize", "pngfilter": units = filtered stream bytes).
+ * "decide", "stuff", "resize", "pngfilter": units = filtered stream bytes;
+ * "count": the list-length pass behind an FDCT; "bound": no launches, units =
+ * images whose cached probe the probe bound decided).
  * Enabling adds one event pair per launch. */
 icx_status icx_profile_enable(icx_ctx* ctx, int32_t on);
 icx_status icx_profile_reset(icx_ctx* ctx);
